@@ -13,10 +13,13 @@ generation + 64x64 render into the HBM-resident observation tensor.
 
 Each rank owns the contiguous global env range [rank*E, (rank+1)*E) (level-seed draws of
 the global index, vecgame.cpp:349-362); there is no data-path collective (weak scaling).
-Rank 0 prints ONE JSON line.  Extra fields: ``roofline`` (12,288 algorithmic bytes per env-step,
-SURVEY.md section 8(d), over the dominant kernel's average duration; the render kernel -- the obs
-writer -- and the whole step beside it) and ``cpu_baseline`` (the CPU oracle on this host's cores,
-bounded sample).
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints the
+headline fields (``value``, ``ms_per_step``, ...).  ``--full`` adds the legs that take work of their
+own: ``roofline`` (12,288 algorithmic bytes per env-step, SURVEY.md section 8(d), over the dominant
+kernel's average duration; the render kernel -- the obs writer -- and the whole step beside it),
+``host_path`` (the host-buffer contract, PCIe included) and ``cpu_baseline`` (the CPU oracle on this
+host's cores, bounded sample).  ``--dump-outputs DIR`` writes what the last timed step computed
+(dump_outputs below) as DIR/<name>.npy, identical from run to run for the same arguments.
 """
 import argparse
 import glob
@@ -134,6 +137,30 @@ def host_path_rate(game, num_levels, E, steps):
                     "buffers, no host copies); pcie_d2h_GBps: a plain 805 MB device -> pinned copy"}
 
 
+DUMP_OBS_ENVS = 1024  # sampled observations: 1024 x 12,288 float32 = 50 MB (all dumps stay under 64 MB)
+
+
+def dump_outputs(env, out_dir):
+    """What a caller of the timed path holds after its last step, as float32 (level seeds: float64) .npy files: `rew`, `first`
+    and the info arrays of every env, the observations of a fixed seeded sample of DUMP_OBS_ENVS envs
+    (`obs_env_ids`, `obs`), and every env's observation as the device-computed 64-bit digest
+    (read_outputs), split into four 16-bit words so that float32 holds it exactly (`obs_digest`)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    E = env.num
+    ids = np.sort(np.random.RandomState(0).choice(E, size=min(E, DUMP_OBS_ENVS), replace=False)).astype(np.int32)
+    sample = env.read_envs(ids)
+    full = env.read_outputs()
+    words = (full["obs_digest"][:, None] >> (np.arange(4, dtype=np.uint64) * np.uint64(16))) & np.uint64(0xFFFF)
+    arrays = {"obs": sample["rgb"], "obs_env_ids": ids, "obs_digest": words, "rew": full["rew"], "first": full["first"],
+              "prev_level_seed": full["prev_level_seed"], "prev_level_complete": full["prev_level_complete"],
+              "level_seed": full["level_seed"]}
+    for name, a in arrays.items():
+        # level seeds are < 2^31 but not < 2^24: float64 keeps them exact
+        dt = np.float64 if a.dtype == np.int32 else np.float32
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(dt))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -144,12 +171,19 @@ def main():
                     help="game (or comma list = mixed batch); the headline metric is coinrun (BASELINE configs[1])")
     ap.add_argument("--num-levels", type=int, default=None,
                     help="default: 200 for coinrun (configs[1]), 0 = unbounded otherwise (SURVEY 8d)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also report roofline (per-kernel times, counter traffic), host_path and cpu_baseline; "
+                         "a plain run reports the headline figure alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs (rew, first, info arrays, "
+                         "a seeded sample of observations, every observation's digest) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
     ap.add_argument("--settle", type=int, default=300,
                     help="untimed steps after the warmup so that episodes, resets and entity lists reach "
                          "steady state before the timed window (reported as settle_steps)")
     ap.add_argument("--host-steps", type=int, default=24,
-                    help="steps of the host-buffer (libenv observe -> numpy) path reported as host_path; 0 = skip")
+                    help="with --full: steps of the host-buffer (libenv observe -> numpy) path reported as host_path; "
+                         "0 = skip")
     ap.add_argument("--gather", action="store_true",
                     help="after every step, RCCL all-gather of every rank's uint8[E,64,64,3] obs shard into a "
                          "[N*E,64,64,3] tensor on each rank (north star's obs concatenation; SURVEY 8(e))")
@@ -231,12 +265,17 @@ def main():
     value = total_steps / elapsed
     ms_per_step = elapsed * 1000 / args.steps
 
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(env, args.dump_outputs)
+
     if rank == 0:
         names = ["pg_step_kernel", "pg_reset_kernel", "pg_render_kernel"]
         mixed = len(game.split(",")) > 1
         parts = env.num_parts()  # a single game's act split into chains over env ranges (kernel_times: per part)
         algo_bytes = E * OBS_BYTES // parts  # every env's 64x64x3 obs write, per launch (one part's envs)
-        if not mixed:
+        if not args.full:
+            roof = None  # the kernel events above stay in the timed path either way: `value` keeps its meaning
+        elif not mixed:
             # 12,288 algorithmic bytes per env-step (the obs write), E env-steps per
             # launch; `achieved` divides them by the DOMINANT kernel's average in-bench duration (HIP
             # events on the engine stream), and the render kernel (the obs writer itself) and the
@@ -286,13 +325,13 @@ def main():
                                   "per_game": {g: [round(x, 4) for x in v] for g, v in kt_games.items()}},
                     "timed_launches": n_timed}
         host = None
-        if args.host_steps > 0 and world == 1:
+        if args.full and args.host_steps > 0 and world == 1:
             try:
                 host = host_path_rate(game, num_levels, E, args.host_steps)
             except Exception as e:
                 host = {"error": repr(e)}
         cpu = None
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             try:
                 cpu = cpu_baseline(game.split(",")[0], num_levels)
             except Exception as e:  # the baseline must never hide the GPU number
@@ -310,6 +349,7 @@ def main():
                        "parallelism": "env-sharded x%d" % world,
                        "gather": ("double-buffered rccl all_gather_into_tensor of obs on a comm stream, "
                                   "%d B per rank per step" % (E * OBS_BYTES)) if args.gather else None},
+            "full": args.full,  # roofline, host_path and cpu_baseline are measured under --full only
             "roofline": roof,
             "host_path": host,
             "cpu_baseline": cpu,

@@ -95,8 +95,18 @@ def test_make_env_render_modes():
     for kw in ({"render_mode": "human"}, {"render": True}):
         with pytest.raises(NotImplementedError):
             make_env(env_name="coinrun", **kw)
-    with pytest.raises((ProcgenError, ValueError, RuntimeError)):
-        make_env(env_name="starpilot", render_mode="rgb_array")  # rotated sprites: not built
+    # rgb_array is built for all 16 games: with a GPU the env comes up and render() hands back the
+    # 512x512 info["rgb"] frame; without one libenv_make fails with the engine's own error
+    from conftest import has_gpu
+    if has_gpu():
+        env = make_env(env_name="starpilot", render_mode="rgb_array")
+        env.reset()
+        frame = env.render()
+        env.close()
+        assert frame.shape == (512, 512, 3) and frame.dtype == np.uint8
+    else:
+        with pytest.raises((ProcgenError, ValueError, RuntimeError)):
+            make_env(env_name="starpilot", render_mode="rgb_array")
     with pytest.raises(Exception):
         make_env(env_name="coinrun", render_mode="bogus")
     assert ToBaselinesVecEnv.metadata["render.modes"] == ["rgb_array"]
