@@ -83,6 +83,9 @@ LIBENV_API int procgen_shard_plan(const char *env_names, int num_envs, int env_o
 /* Copy the outputs of `count` envs (ids env_ids[k]) to host arrays of `count` rows after the
  * enqueued steps finish; any pointer may be NULL.  For consumers (and tests) that sample a few
  * envs of a device-resident batch without copying the whole observation tensor. */
+LIBENV_API int procgen_read_envs(libenv_env *env, const int32_t *env_ids, int count, uint8_t *rgb, float *rew,
+                                 uint8_t *first, int32_t *prev_level_seed, uint8_t *prev_level_complete,
+                                 int32_t *level_seed);
 /* The outputs of EVERY env after the enqueued steps finish, for parity checks of whole populations
  * (tests/test_gpu_population.py): obs_digest[e] = sum over k < 1536 of w_k * x_k mod 2^64, x_k the
  * k-th little-endian 64-bit word of env e's 64x64x3 observation and w_k = splitmix64(k) | 1 (the
@@ -90,9 +93,6 @@ LIBENV_API int procgen_shard_plan(const char *env_names, int num_envs, int env_o
  * Host arrays of num_envs entries; any may be NULL.  Returns 0 on success. */
 LIBENV_API int procgen_read_outputs(libenv_env *env, uint64_t *obs_digest, float *rew, uint8_t *first,
                                     int32_t *prev_level_seed, uint8_t *prev_level_complete, int32_t *level_seed);
-LIBENV_API int procgen_read_envs(libenv_env *env, const int32_t *env_ids, int count, uint8_t *rgb, float *rew,
-                                 uint8_t *first, int32_t *prev_level_seed, uint8_t *prev_level_complete,
-                                 int32_t *level_seed);
 /* Build the atlas libenv_make would load for `env_name` (comma list) from `resource_root` (NULL or
  * "" = the package's assets directory) on the host only: returns the pixel count (copied into
  * `pixels` when capacity allows) and fills the tables (layouts as procgen_upload_atlas); < 0 on
@@ -105,6 +105,33 @@ LIBENV_API int64_t procgen_atlas_host(const char *env_name, const char *resource
  * agent).  libenv's get_state / set_state use the upstream byte format (pg_state.cpp). */
 LIBENV_API int procgen_get_snapshot(libenv_env *env, int env_idx, char *data, int length);
 LIBENV_API void procgen_set_snapshot(libenv_env *env, int env_idx, const char *data, int length);
+
+/* Device-resident snapshots: env states saved, restored and copied between envs without leaving
+ * device memory (csrc/pg_snapshot.hip).  A store is `capacity` slots of procgen_store_slot_bytes()
+ * each, owned by `env` (libenv_close frees it); a slot holds what procgen_get_snapshot holds (the
+ * scalars, the live entity slots, the grid with its int8 mirror, both generators, the latent row of
+ * maze / miner, the generated background).  env_ids, slots, src_ids and dst_ids are host arrays of
+ * `count` entries.
+ *   save:  slot slots[k] becomes the state of env env_ids[k].
+ *   load:  env env_ids[k] becomes the state in slot slots[k]: its frame is re-rendered (the loaded
+ *          envs only, into the bound observation buffer) and its reward / first / level-seed outputs
+ *          are those of the state's last step, as after set_state.
+ *   fork:  env dst_ids[k] becomes a copy of env src_ids[k] as it was BEFORE the call (dst may overlap
+ *          src: a swap or a permutation is valid).
+ * Every call is ordered on the env's stream after the steps already enqueued and before later ones,
+ * and returns without waiting for it (it blocks only on the upload of its id lists);
+ * procgen_store_free waits for the kernels still using the store.  One slot may be loaded into many
+ * envs and one env forked many ways, but a destination -- an env id of load / fork, a slot of save
+ * -- named twice in one call, an id out of range, an empty slot, or a state of another game than the
+ * env's slot of a mixed batch is rejected before any env is touched (sticky PG_ERR_BAD_OPTION).
+ * create returns the store id (>= 0); the others 0; all < 0 on error. */
+LIBENV_API int procgen_store_create(libenv_env *env, int capacity);
+LIBENV_API int procgen_store_free(libenv_env *env, int store);
+LIBENV_API int procgen_store_save(libenv_env *env, int store, const int32_t *env_ids, const int32_t *slots, int count);
+LIBENV_API int procgen_store_load(libenv_env *env, int store, const int32_t *slots, const int32_t *env_ids, int count);
+LIBENV_API int procgen_fork_envs(libenv_env *env, const int32_t *src_ids, const int32_t *dst_ids, int count);
+/* Device memory one slot takes (fixed per env handle: sized for the largest world of its games). */
+LIBENV_API int64_t procgen_store_slot_bytes(libenv_env *env);
 
 /* Pinning helper: RandGen::serialize's text (randgen.cpp:100-106) of 624 MT words + position. */
 LIBENV_API int procgen_mt_text(const uint32_t *words, int pos, char *out, int length);

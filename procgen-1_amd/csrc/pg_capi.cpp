@@ -26,6 +26,7 @@
 #include "pg_assets.h"
 #include "pg_state.h"
 #include "pg_engine.h"
+#include "pg_snapshot.h"
 
 extern "C" {
 void pg_launch_step(const PGDev *d, int game, const int32_t *env_list, int count, hipStream_t s, int use_hash,
@@ -302,7 +303,34 @@ void build_rot_table(float *angles, double *table) {
     }
 }
 
+// A snapshot store (procgen_store_*): `capacity` slots of the handle's slot stride in one device
+// allocation, and what the host checks a load against without reading the device
+struct SnapStore {
+    uint8_t *mem = nullptr;
+    int capacity = 0;
+    std::vector<uint8_t> filled, rf_bad; // per slot: holds a state; that state is one the register-frame render
+                                         // cannot draw (VecEnv::rf_bad of the env it was saved from)
+    std::vector<int8_t> game;            // per slot: game id of the state
+};
+// One device buffer of the (env, slot) id lists of a store call; `used` marks its last reader on the
+// engine stream, so a later call reuses it only after that kernel ran
+struct SnapIds {
+    int32_t *d = nullptr;
+    size_t cap = 0;
+    hipEvent_t used = nullptr;
+    bool pending = false;
+};
+#define PG_SNAP_IDS 4
+
 struct VecEnv {
+    // device-resident snapshots (pg_snapshot.hip): stores by id (freed ones stay null), the scratch store
+    // of procgen_fork_envs, the id-list ring and the stream its uploads run on (created on first use)
+    std::vector<SnapStore *> stores;
+    SnapStore *fork_scratch = nullptr;
+    SnapIds snap_ids[PG_SNAP_IDS];
+    unsigned snap_next = 0;
+    hipStream_t ustream = nullptr;
+    PGSnapLayout snap_lay{};
     uint64_t *d_digest = nullptr; // procgen_read_outputs' per-env observation digests (allocated on first use)
     int rf_make = 0;               // PGDev::render_rf chosen at make time
     std::vector<uint8_t> rf_bad;   // [num_envs] env holds a restored state the register-frame render cannot draw
@@ -1660,6 +1688,20 @@ LIBENV_API void libenv_close(libenv_env *env) {
     if (v->hstream) (void)hipStreamSynchronize(v->hstream);
     if (v->stream) (void)hipStreamSynchronize(v->stream);
     unregister_buffers(v);
+    for (SnapStore *st : v->stores)
+        if (st) {
+            (void)hipFree(st->mem);
+            delete st;
+        }
+    if (v->fork_scratch) {
+        (void)hipFree(v->fork_scratch->mem);
+        delete v->fork_scratch;
+    }
+    for (auto &b : v->snap_ids) {
+        if (b.d) (void)hipFree(b.d);
+        if (b.used) (void)hipEventDestroy(b.used);
+    }
+    if (v->ustream) (void)hipStreamDestroy(v->ustream);
     for (void *p : v->allocs) hipFree(p);
     if (v->d_digest) (void)hipFree(v->d_digest);
     if (v->pinned) (void)hipHostFree(v->pinned);
@@ -2286,6 +2328,255 @@ LIBENV_API void set_state(libenv_env *env, int env_idx, char *data, int length) 
         return;
     }
     write_host_env(v, env_idx, h);
+}
+
+// ---- device-resident snapshots (pg_snapshot.hip, pg_snapshot.h): env states saved to,
+// restored from and copied between envs through slots in device memory.  Every call enqueues on the
+// engine stream (the act joined every chain back into it) and returns without waiting for it; the id
+// lists go up on a stream of their own, whose small copy is all a call blocks on.
+static const PGSnapLayout &snap_layout(VecEnv *v) {
+    if (!v->snap_lay.slot_bytes)
+        v->snap_lay = pg_snap_layout(v->games.data(), (int)v->games.size(), v->has_latent, v->dev.gen_bg != nullptr);
+    return v->snap_lay;
+}
+
+static SnapStore *snap_new(VecEnv *v, int capacity) {
+    void *mem = nullptr;
+    const size_t bytes = (size_t)capacity * snap_layout(v).slot_bytes;
+    if (hipMalloc(&mem, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        return nullptr;
+    }
+    SnapStore *st = new SnapStore;
+    st->mem = (uint8_t *)mem;
+    st->capacity = capacity;
+    st->filled.assign((size_t)capacity, 0);
+    st->rf_bad.assign((size_t)capacity, 0);
+    st->game.assign((size_t)capacity, -1);
+    return st;
+}
+
+// The id lists of one call on the device: the next buffer of the ring, once its last reader ran
+static int snap_upload(VecEnv *v, const std::vector<int32_t> &h, SnapIds **out) {
+    SnapIds &b = v->snap_ids[v->snap_next++ % PG_SNAP_IDS];
+    if (b.pending) {
+        HIPCHECK(hipEventSynchronize(b.used));
+        b.pending = false;
+    }
+    if (b.cap < h.size()) {
+        if (b.d) (void)hipFree(b.d);
+        b.d = nullptr;
+        b.cap = 0;
+        size_t cap = 1024;
+        while (cap < h.size()) cap *= 2;
+        HIPCHECK(hipMalloc((void **)&b.d, cap * 4));
+        b.cap = cap;
+    }
+    if (!b.used) HIPCHECK(hipEventCreateWithFlags(&b.used, hipEventDisableTiming));
+    if (!v->ustream) HIPCHECK(hipStreamCreateWithFlags(&v->ustream, hipStreamNonBlocking));
+    HIPCHECK(hipMemcpyAsync(b.d, h.data(), h.size() * 4, hipMemcpyHostToDevice, v->ustream));
+    HIPCHECK(hipStreamSynchronize(v->ustream));
+    *out = &b;
+    return 0;
+}
+
+static PGSnap snap_args(VecEnv *v, SnapStore *st, const int32_t *d_env_ids, const int32_t *d_slots, int count) {
+    const PGDev &d = v->dev;
+    PGSnap a{};
+    a.envs = d.envs; a.ents = d.ents; a.grid = d.grid; a.grid8 = d.grid8; a.mt = d.mt;
+    a.latent = d.latent; a.gen_bg = d.gen_bg;
+    a.rew = d.rew; a.first = d.first; a.prev_level_seed = d.prev_level_seed;
+    a.prev_level_complete = d.prev_level_complete; a.level_seed = d.level_seed;
+    a.sp_gen = v->prefetch ? d.sp_gen : nullptr;
+    a.store = st->mem;
+    a.lay = snap_layout(v);
+    a.env_ids = d_env_ids; a.slots = d_slots; a.count = count;
+    return a;
+}
+
+// env_ids[k] -> slot slots[k] (arguments already checked)
+static int snap_save(VecEnv *v, SnapStore *st, const int32_t *env_ids, const int32_t *slots, int count) {
+    std::vector<int32_t> h(env_ids, env_ids + count);
+    h.insert(h.end(), slots, slots + count);
+    SnapIds *b = nullptr;
+    if (int rc = snap_upload(v, h, &b)) return rc;
+    const PGSnap a = snap_args(v, st, b->d, b->d + count, count);
+    pg_launch_snapshot(&a, 0, v->stream);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipEventRecord(b->used, v->stream));
+    b->pending = true;
+    for (int k = 0; k < count; k++) {
+        st->filled[(size_t)slots[k]] = 1;
+        st->game[(size_t)slots[k]] = (int8_t)v->game_of(env_ids[k]);
+        st->rf_bad[(size_t)slots[k]] = v->rf_bad[(size_t)env_ids[k]];
+    }
+    return 0;
+}
+
+// slot slots[k] -> env_ids[k] (arguments already checked), then what procgen_set_snapshot does to a
+// restored env: the kernel writes its output scalars and drops its spare; the host keeps the
+// register-frame bookkeeping and re-renders the loaded envs only, one launch per game
+static int snap_load(VecEnv *v, SnapStore *st, const int32_t *slots, const int32_t *env_ids, int count) {
+    const size_t G = v->games.size();
+    std::vector<int32_t> h(env_ids, env_ids + count);
+    h.insert(h.end(), slots, slots + count);
+    std::vector<int> lo(G + 1, 0); // game k's loaded envs: h[2 * count + lo[k] .. lo[k + 1]) (one game: the ids themselves)
+    if (G > 1) {
+        for (size_t k = 0; k < G; k++) {
+            for (int i = 0; i < count; i++)
+                if (v->game_of(env_ids[i]) == v->games[k]) h.push_back(env_ids[i]);
+            lo[k + 1] = (int)h.size() - 2 * count;
+        }
+    } else {
+        lo[1] = count;
+    }
+    SnapIds *b = nullptr;
+    if (int rc = snap_upload(v, h, &b)) return rc;
+    const PGSnap a = snap_args(v, st, b->d, b->d + count, count);
+    pg_launch_snapshot(&a, 1, v->stream);
+    for (int k = 0; k < count; k++) { // a restored env draws with the options its state carries (procgen_set_snapshot)
+        const size_t e = (size_t)env_ids[k];
+        const uint8_t bad = st->rf_bad[(size_t)slots[k]];
+        if (bad != v->rf_bad[e]) {
+            v->rf_bad_n[v->game_of((int)e)] += bad ? 1 : -1;
+            v->rf_bad[e] = bad;
+        }
+    }
+    int off = 0;
+    for (int g = 0; g < PG_NUM_GAMES; g++)
+        if (v->rf_bad_n[g] > 0) off |= 1 << g;
+    v->dev.render_rf = v->rf_make & ~off;
+    for (size_t k = 0; k < G; k++) {
+        PG_POISON(v->stream);
+        pg_launch_render(&v->dev, v->games[k], G > 1 ? b->d + 2 * count + lo[k] : b->d, lo[k + 1] - lo[k], v->stream, 0,
+                         v->games[k]);
+    }
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipEventRecord(b->used, v->stream));
+    b->pending = true;
+    v->obs_inflight = false; // an act's early obs DMA predates these frames: observe copies again
+    return 0;
+}
+
+static SnapStore *snap_store_of(VecEnv *v, int store) {
+    return store >= 0 && (size_t)store < v->stores.size() ? v->stores[(size_t)store] : nullptr;
+}
+
+// ids[k] in [0, n) for every k; with `unique`, no id twice
+static bool snap_ids_ok(const int32_t *ids, int count, int n, bool unique) {
+    std::vector<uint8_t> seen(unique ? (size_t)n : 0, 0);
+    for (int k = 0; k < count; k++) {
+        if (ids[k] < 0 || ids[k] >= n) return false;
+        if (unique) {
+            if (seen[(size_t)ids[k]]) return false;
+            seen[(size_t)ids[k]] = 1;
+        }
+    }
+    return true;
+}
+
+LIBENV_API int procgen_store_create(libenv_env *env, int capacity) {
+    VecEnv *v = (VecEnv *)env;
+    if (!v) return -PG_ERR_BAD_OPTION; // a closed / never-made env
+    if (capacity <= 0) return fail(v, PG_ERR_BAD_OPTION, "procgen_store_create: capacity must be positive");
+    HIPCHECK(hipSetDevice(v->device));
+    SnapStore *st = snap_new(v, capacity);
+    if (!st) return fail(v, PG_ERR_HIP, "procgen_store_create: out of device memory");
+    for (size_t i = 0; i < v->stores.size(); i++)
+        if (!v->stores[i]) {
+            v->stores[i] = st;
+            return (int)i;
+        }
+    v->stores.push_back(st);
+    return (int)v->stores.size() - 1;
+}
+
+LIBENV_API int procgen_store_free(libenv_env *env, int store) {
+    VecEnv *v = (VecEnv *)env;
+    if (!v) return -PG_ERR_BAD_OPTION; // a closed / never-made env
+    SnapStore *st = snap_store_of(v, store);
+    if (!st) return fail(v, PG_ERR_BAD_OPTION, "procgen_store_free: no such store");
+    HIPCHECK(hipSetDevice(v->device));
+    HIPCHECK(hipFree(st->mem)); // waits for the kernels that still use the slots
+    delete st;
+    v->stores[(size_t)store] = nullptr;
+    return 0;
+}
+
+LIBENV_API int64_t procgen_store_slot_bytes(libenv_env *env) {
+    VecEnv *v = (VecEnv *)env;
+    if (!v) return -PG_ERR_BAD_OPTION; // a closed / never-made env
+    return (int64_t)snap_layout(v).slot_bytes;
+}
+
+LIBENV_API int procgen_store_save(libenv_env *env, int store, const int32_t *env_ids, const int32_t *slots, int count) {
+    VecEnv *v = (VecEnv *)env;
+    if (!v) return -PG_ERR_BAD_OPTION; // a closed / never-made env
+    SnapStore *st = snap_store_of(v, store);
+    if (!st) return fail(v, PG_ERR_BAD_OPTION, "procgen_store_save: no such store");
+    if (!v->started) return fail(v, PG_ERR_BAD_OPTION, "procgen_store_save: before the first reset");
+    if (count < 0 || (count > 0 && (!env_ids || !slots))) return fail(v, PG_ERR_BAD_OPTION, "procgen_store_save: bad arguments");
+    if (!snap_ids_ok(env_ids, count, v->num_envs, false))
+        return fail(v, PG_ERR_BAD_OPTION, "procgen_store_save: env id out of range");
+    if (!snap_ids_ok(slots, count, st->capacity, true))
+        return fail(v, PG_ERR_BAD_OPTION, "procgen_store_save: slot out of range or named twice");
+    if (count == 0) return 0;
+    HIPCHECK(hipSetDevice(v->device));
+    return snap_save(v, st, env_ids, slots, count);
+}
+
+LIBENV_API int procgen_store_load(libenv_env *env, int store, const int32_t *slots, const int32_t *env_ids, int count) {
+    VecEnv *v = (VecEnv *)env;
+    if (!v) return -PG_ERR_BAD_OPTION; // a closed / never-made env
+    SnapStore *st = snap_store_of(v, store);
+    if (!st) return fail(v, PG_ERR_BAD_OPTION, "procgen_store_load: no such store");
+    if (!v->started) return fail(v, PG_ERR_BAD_OPTION, "procgen_store_load: before the first reset");
+    if (count < 0 || (count > 0 && (!env_ids || !slots))) return fail(v, PG_ERR_BAD_OPTION, "procgen_store_load: bad arguments");
+    if (!snap_ids_ok(slots, count, st->capacity, false))
+        return fail(v, PG_ERR_BAD_OPTION, "procgen_store_load: slot out of range");
+    if (!snap_ids_ok(env_ids, count, v->num_envs, true))
+        return fail(v, PG_ERR_BAD_OPTION, "procgen_store_load: env id out of range or named twice");
+    for (int k = 0; k < count; k++) {
+        if (!st->filled[(size_t)slots[k]]) return fail(v, PG_ERR_BAD_OPTION, "procgen_store_load: the slot holds no state");
+        // the reference: fassert(game_name == b->read_string()), game.cpp:259
+        if (st->game[(size_t)slots[k]] != v->game_of(env_ids[k]))
+            return fail(v, PG_ERR_BAD_OPTION, "procgen_store_load: the state belongs to another game than this env slot");
+    }
+    if (count == 0) return 0;
+    HIPCHECK(hipSetDevice(v->device));
+    return snap_load(v, st, slots, env_ids, count);
+}
+
+LIBENV_API int procgen_fork_envs(libenv_env *env, const int32_t *src_ids, const int32_t *dst_ids, int count) {
+    VecEnv *v = (VecEnv *)env;
+    if (!v) return -PG_ERR_BAD_OPTION; // a closed / never-made env
+    if (!v->started) return fail(v, PG_ERR_BAD_OPTION, "procgen_fork_envs: before the first reset");
+    if (count < 0 || (count > 0 && (!src_ids || !dst_ids))) return fail(v, PG_ERR_BAD_OPTION, "procgen_fork_envs: bad arguments");
+    if (!snap_ids_ok(src_ids, count, v->num_envs, false))
+        return fail(v, PG_ERR_BAD_OPTION, "procgen_fork_envs: source env id out of range");
+    if (!snap_ids_ok(dst_ids, count, v->num_envs, true))
+        return fail(v, PG_ERR_BAD_OPTION, "procgen_fork_envs: destination env id out of range or named twice");
+    for (int k = 0; k < count; k++)
+        if (v->game_of(src_ids[k]) != v->game_of(dst_ids[k]))
+            return fail(v, PG_ERR_BAD_OPTION, "procgen_fork_envs: source and destination play different games");
+    if (count == 0) return 0;
+    HIPCHECK(hipSetDevice(v->device));
+    // through the scratch store, so dst may overlap src: every source is saved before any env is written
+    if (!v->fork_scratch || v->fork_scratch->capacity < count) {
+        int cap = 64;
+        while (cap < count) cap *= 2;
+        SnapStore *st = snap_new(v, cap);
+        if (!st) return fail(v, PG_ERR_HIP, "procgen_fork_envs: out of device memory");
+        if (v->fork_scratch) {
+            (void)hipFree(v->fork_scratch->mem); // waits for the forks that still use it
+            delete v->fork_scratch;
+        }
+        v->fork_scratch = st;
+    }
+    std::vector<int32_t> slots((size_t)count);
+    for (int k = 0; k < count; k++) slots[(size_t)k] = k;
+    if (int rc = snap_save(v, v->fork_scratch, src_ids, slots.data(), count)) return rc;
+    return snap_load(v, v->fork_scratch, slots.data(), dst_ids, count);
 }
 
 } // extern "C"

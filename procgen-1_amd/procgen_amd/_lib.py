@@ -92,6 +92,12 @@ SIGNATURES = {
     "procgen_debug_env": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int]),
     "procgen_profile_read": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "procgen_profile_raw": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "procgen_store_create": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+    "procgen_store_free": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+    "procgen_store_save": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]),
+    "procgen_store_load": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]),
+    "procgen_fork_envs": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]),
+    "procgen_store_slot_bytes": (ctypes.c_int64, [ctypes.c_void_p]),
     "procgen_selftest_libm": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
                                              ctypes.c_void_p]),
 }

@@ -82,6 +82,61 @@ def _check(lib, handle, rc=0):
         raise ProcgenError("procgen_mi355x error %d: %s" % (err or -rc, msg.decode() if msg else ""))
 
 
+def _ids(x):
+    return np.ascontiguousarray(x, dtype=np.int32).reshape(-1)
+
+
+class SnapshotStore:
+    """`capacity` env states in device memory (procgen_store_*), made by ``env.snapshot_store``.
+    ``save(env_ids, slots)`` copies envs into slots and ``load(slots, env_ids)`` slots into envs, on the
+    env's stream and without a host round trip; a slot may be loaded into many envs.  The store lives
+    until ``close()`` or the env's ``close()``."""
+
+    def __init__(self, env, capacity):
+        self._env = env
+        self.capacity = int(capacity)
+        rc = env._lib.procgen_store_create(env._handle, self.capacity)
+        _check(env._lib, env._handle, rc)
+        self._id = rc
+        self.slot_bytes = int(env._lib.procgen_store_slot_bytes(env._handle))
+
+    def _live(self):
+        if self._id is None or not self._env.is_open():
+            raise ProcgenError("snapshot store is closed")
+        return self._env
+
+    def save(self, env_ids, slots):
+        env = self._live()
+        e, s = _ids(env_ids), _ids(slots)
+        if e.size != s.size:
+            raise ProcgenError("save: %d env ids for %d slots" % (e.size, s.size))
+        rc = env._lib.procgen_store_save(env._handle, self._id, e.ctypes.data, s.ctypes.data, e.size)
+        _check(env._lib, env._handle, rc)
+
+    def load(self, slots, env_ids):
+        env = self._live()
+        s, e = _ids(slots), _ids(env_ids)
+        if e.size != s.size:
+            raise ProcgenError("load: %d slots for %d env ids" % (s.size, e.size))
+        rc = env._lib.procgen_store_load(env._handle, self._id, s.ctypes.data, e.ctypes.data, e.size)
+        _check(env._lib, env._handle, rc)
+        env._after_restore()
+
+    def save_all(self):
+        """Env e into slot e, for every env (needs capacity >= the env count)."""
+        n = np.arange(self._live().num, dtype=np.int32)
+        self.save(n, n)
+
+    def load_all(self):
+        n = np.arange(self._live().num, dtype=np.int32)
+        self.load(n, n)
+
+    def close(self):
+        if self._id is not None and self._env.is_open():
+            self._env._lib.procgen_store_free(self._env._handle, self._id)
+        self._id = None
+
+
 class BaseProcgenEnv:
     """procgen/env.py:87-227 over libprocgen_mi355x.so."""
 
@@ -264,6 +319,26 @@ class BaseProcgenEnv:
             self._lib.libenv_observe(self._handle)
 
     # ------------------------------------------------------------------ device extensions
+    def snapshot_store(self, capacity):
+        """A SnapshotStore of `capacity` env states in device memory."""
+        return SnapshotStore(self, capacity)
+
+    def fork(self, src_ids, dst_ids):
+        """Env dst_ids[k] becomes a copy of env src_ids[k] as it was before the call, on the device
+        (procgen_fork_envs): dst may overlap src, and one env may be forked many ways."""
+        s, d = _ids(src_ids), _ids(dst_ids)
+        if s.size != d.size:
+            raise ProcgenError("fork: %d sources for %d destinations" % (s.size, d.size))
+        rc = self._lib.procgen_fork_envs(self._handle, s.ctypes.data, d.ctypes.data, s.size)
+        _check(self._lib, self._handle, rc)
+        self._after_restore()
+
+    def _after_restore(self):
+        # as set_state: the host buffers show the restored frames and scalars
+        if not self.device_buffers:
+            self._lib.libenv_observe(self._handle)
+            _check(self._lib, self._handle)
+
     def act_hashed(self, seed, t):
         rc = self._lib.procgen_act_hashed(self._handle, seed, t)
         _check(self._lib, self._handle, rc)
